@@ -29,6 +29,13 @@ device synchronize; time is the max over ranks. ``value`` = total rows x K /
 seconds (whole job). Per-GPU rows are fixed as N grows (weak scaling).
 The secondary metric (N_rows x numIterations / iteration-loop seconds) and a
 per-phase breakdown are reported under ``config``.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K fits, print the result line. ``--full`` adds the sanity check that takes
+work of its own: the holdout AUC of the last model (``config.holdout_auc``,
+null without it). ``--dump-outputs DIR`` writes what the last timed fit
+returned, as ``DIR/<name>.npy`` (see ``model_arrays``): the inputs are seeded,
+so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -63,6 +70,39 @@ def higgs_like(n: int, f: int, seed: int):
     s = s - np.median(s)
     y = (s + 1.2 * rng.standard_normal(n, dtype=np.float32) > 0).astype(np.float32)
     return X, y
+
+
+_TREE_KEYS = ("num_leaves", "shrinkage", "split_feature", "split_gain", "threshold", "decision_type", "left_child",
+              "right_child", "leaf_value", "leaf_weight", "leaf_count", "internal_value", "internal_weight",
+              "internal_count")
+
+
+def model_arrays(text: str) -> dict:
+    """The trees of a LightGBM model text as flat float64 arrays: one ``num_leaves`` / ``shrinkage`` entry per
+    tree, and every per-node / per-leaf field concatenated over the trees in model order."""
+    cols = {k: [] for k in _TREE_KEYS}
+    in_tree = False
+    for line in text.splitlines():
+        if line.startswith("Tree="):
+            in_tree = True
+        elif line.startswith("end of trees"):
+            break
+        elif in_tree and "=" in line:
+            k, v = line.split("=", 1)
+            if k in cols:
+                cols[k].append(np.array(v.split(), dtype=np.float64))
+    return {k: np.concatenate(v) if v else np.zeros(0, np.float64) for k, v in cols.items()}
+
+
+def dump_outputs(d: str, model, p_hold: np.ndarray) -> None:
+    """``--dump-outputs``: the returned model's trees and its probabilities on the seeded holdout rows
+    (float64; ~10^5 numbers per 100 x 31-leaf model plus 200k probabilities, far below 64 MB)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = model_arrays(model.getNativeModel())
+    arrays["holdout_probability"] = np.asarray(p_hold, dtype=np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def _free_port() -> int:
@@ -106,6 +146,10 @@ def main() -> None:
     ap.add_argument("--iterations", type=int, default=100, help="numIterations of each fit (reference default 100)")
     ap.add_argument("--device", default="gpu")
     ap.add_argument("--save-model", default=None, help="write the last model's text here (after timing)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the holdout AUC of the last model")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed fit's model (tree arrays) and its holdout probabilities as DIR/<name>.npy")
     ap.add_argument("--profile", action="store_true", help="cProfile one more fit after timing (stderr, host side)")
     ap.add_argument("--allow-shared-device", action="store_true",
                     help="rehearsal only: allow more ranks than visible GPUs (ranks share devices)")
@@ -214,19 +258,22 @@ def main() -> None:
         phases[k] = round(float(np.mean(vals)), 2) if vals else None
     native_stats = measures[-1].get("native_stats", {}) if measures else {}
     iter_s = (phases["training_iterations_ms"] or 0.0) / 1e3
-    # sanity (outside the timed region): AUC of the last model on 200k fresh rows of the same distribution
-    # (a different seed from every rank's training rows: a real holdout, not a train AUC)
+    # outside the timed region, and only on request: the last model's probabilities on 200k fresh rows of the
+    # same distribution (a different seed from every rank's training rows: a real holdout, not a train AUC)
     auc = None
     n_hold = min(200_000, args.rows)
-    if rank == 0 and model is not None:
-        try:
-            from sklearn.metrics import roc_auc_score
+    if rank == 0 and model is not None and (args.full or args.dump_outputs):
+        X_hold, y_hold = higgs_like(n_hold, args.features, seed=987_654)
+        p_hold = model.getModel().score(X_hold.astype(np.float64), raw=False, classification=True)[:, 1]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, model, p_hold)
+        if args.full:  # sanity: holdout AUC
+            try:
+                from sklearn.metrics import roc_auc_score
 
-            X_hold, y_hold = higgs_like(n_hold, args.features, seed=987_654)
-            p = model.getModel().score(X_hold.astype(np.float64), raw=False, classification=True)[:, 1]
-            auc = float(roc_auc_score(y_hold, p))
-        except Exception:  # pragma: no cover
-            auc = None
+                auc = float(roc_auc_score(y_hold, p_hold))
+            except Exception:  # pragma: no cover
+                auc = None
     if args.save_model and rank == 0 and model is not None:
         with open(args.save_model, "w") as fh:
             fh.write(model.getNativeModel())

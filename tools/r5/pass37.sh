@@ -14,6 +14,6 @@ rm -rf "$OUT/prof_fit"
 head -8 "$OUT/tree_breakdown.txt"
 for v in merged split merged split; do
   if [ $v = split ]; then export SML_GBDT_MERGED_FIND=0; else unset SML_GBDT_MERGED_FIND; fi
-  timeout -k 10 300 python bench.py --steps 5 --warmup 1 > "$OUT/bench_$v.log" 2>&1 || exit 1
+  timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 > "$OUT/bench_$v.log" 2>&1 || exit 1
   echo "$v $(tail -1 "$OUT/bench_$v.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['config']['iteration_ms'], d['config']['holdout_auc'])")"
 done

@@ -8,6 +8,6 @@ tail -1 "$OUT/pytest_gbdt.log"
 for L in 31 255; do
   SML_BPLAN_PROF=1 timeout -k 10 300 python bench.py --steps 1 --warmup 1 --leaves $L > "$OUT/bench_prof_L$L.log" 2> "$OUT/phases_L$L.txt" || exit 1
   echo "L$L $(grep 'bplan phases' "$OUT/phases_L$L.txt" | tail -1)"
-  timeout -k 10 300 python bench.py --steps 3 --warmup 1 --leaves $L > "$OUT/bench_L$L.log" 2>&1 || exit 1
+  timeout -k 10 300 python bench.py --full --steps 3 --warmup 1 --leaves $L > "$OUT/bench_L$L.log" 2>&1 || exit 1
   echo "leaves $L: $(tail -1 "$OUT/bench_L$L.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['config']['iteration_ms'], round(d['config']['holdout_auc'], 5))")"
 done
