@@ -114,6 +114,38 @@ PYBIND11_MODULE(_nn, m) {
      pybind11::arg("alpha"), pybind11::arg("beta"), pybind11::arg("bias"), pybind11::arg("cmat"), pybind11::arg("ldcm"),
      pybind11::arg("scm"), pybind11::arg("act"), pybind11::arg("dtype"), pybind11::arg("stream"),
      pybind11::arg("conv") = std::vector<int>(), pybind11::arg("stride_bias") = 0);
+  // quantised GEMM / conv (K18). ptrs: a_zp, b_zp, a_scale, b_scale, y_scale, y_zp, bias (0 = absent);
+  // flags: trans_b, a_signed, b_signed, out (0 int32, 1 u8, 2 s8), a_zp_stride, b_zp_stride, b_scale_stride;
+  // conv as in gemm. Returns false when the kernel does not take the shape (nothing was launched).
+  m.def("qgemm", [](uintptr_t a, uintptr_t b, uintptr_t c, int M, int N, int K, int batch, int64_t lda, int64_t ldb,
+                    int64_t ldc, int64_t sa, int64_t sb, int64_t sc, std::vector<int> flags,
+                    std::vector<uintptr_t> ptrs, int64_t stride_n, uintptr_t stream, std::vector<int> conv) {
+    if (flags.size() != 7 || ptrs.size() != 7) throw std::invalid_argument("qgemm: 7 flags, 7 pointers");
+    QGemmArgs g;
+    if (!conv.empty()) {
+      if (conv.size() != 13) throw std::invalid_argument("conv geometry: H,W,C,R,S,sh,sw,ph,pw,dh,dw,OH,OW");
+      g.conv = 1;
+      g.H = conv[0]; g.W = conv[1]; g.C = conv[2]; g.R = conv[3]; g.S = conv[4]; g.stride_h = conv[5];
+      g.stride_w = conv[6]; g.pad_h = conv[7]; g.pad_w = conv[8]; g.dil_h = conv[9]; g.dil_w = conv[10];
+      g.OH = conv[11]; g.OW = conv[12];
+    }
+    g.a = P<const void>(a); g.b = P<const void>(b); g.c = P<void>(c);
+    g.M = M; g.N = N; g.K = K; g.batch = batch;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.stride_a = sa; g.stride_b = sb; g.stride_c = sc;
+    g.trans_b = flags[0]; g.a_signed = flags[1]; g.b_signed = flags[2]; g.out = flags[3];
+    g.a_zp_stride = flags[4]; g.b_zp_stride = flags[5]; g.b_scale_stride = flags[6];
+    g.a_zp = P<const void>(ptrs[0]); g.b_zp = P<const void>(ptrs[1]); g.a_scale = P<const float>(ptrs[2]);
+    g.b_scale = P<const float>(ptrs[3]); g.y_scale = P<const float>(ptrs[4]); g.y_zp = P<const void>(ptrs[5]);
+    g.bias = P<const int32_t>(ptrs[6]);
+    g.stride_n = stride_n;
+    const int rc = QGemmMfma(g, P<void>(stream));
+    if (rc == -4) return false;
+    if (rc != 0) throw std::runtime_error("qgemm_mfma failed (rc=" + std::to_string(rc) + ")");
+    return true;
+  }, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("c"), pybind11::arg("M"), pybind11::arg("N"),
+     pybind11::arg("K"), pybind11::arg("batch"), pybind11::arg("lda"), pybind11::arg("ldb"), pybind11::arg("ldc"),
+     pybind11::arg("sa"), pybind11::arg("sb"), pybind11::arg("sc"), pybind11::arg("flags"), pybind11::arg("ptrs"),
+     pybind11::arg("stride_n"), pybind11::arg("stream"), pybind11::arg("conv") = std::vector<int>());
   m.def("group_conv", [](uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t bias, uintptr_t res, std::vector<int> g,
                          int groups, int relu, int dtype, uintptr_t stream) {
     if (g.size() != 15) throw std::invalid_argument("geometry: B,H,W,C,Cout,R,S,sh,sw,ph,pw,dh,dw,OH,OW");

@@ -80,6 +80,41 @@ struct GemmArgs {
   int OH = 0, OW = 0;
 };
 int GemmMfma(const GemmArgs& g, int dtype, void* stream);
+// K18: quantised batched GEMM / implicit-GEMM convolution on the int8 MFMA (qgemm_mfma.hip):
+//   acc[m, n] = sum_k (A[m, k] - a_zp[m]) * (B[k, n] - b_zp[n]) (+ bias[n]);  out = acc (int32) or
+//   sat(rint(double(acc) * (double(a_scale) * double(b_scale[n])) / double(y_scale)) + y_zp) (u8 / s8).
+// A is [M][K] (lda >= K) u8 or s8; B is stored [K][N] (trans_b = 0, ldb >= N) or [N][K] (trans_b = 1).
+// Zero points, scales and bias are device pointers read by the kernel (a zero point has its operand's
+// type; a *_stride of 0 is a scalar, 1 a vector per row of A / per column of B). Batch strides are in
+// elements (0 = broadcast); batch z reads the per-column vectors at z * stride_n. K <= 32768.
+// Returns 0, or < 0 when the shape is not supported (-4: K or the batch is out of range).
+struct QGemmArgs {
+  const void* a = nullptr;
+  const void* b = nullptr;
+  void* c = nullptr;
+  int M = 0, N = 0, K = 0, batch = 1;
+  int64_t lda = 0, ldb = 0, ldc = 0;
+  int64_t stride_a = 0, stride_b = 0, stride_c = 0;
+  int trans_b = 0;
+  int a_signed = 0, b_signed = 0;
+  int out = 0;                       // 0 int32, 1 u8, 2 s8
+  const void* a_zp = nullptr;        // null: 0
+  const void* b_zp = nullptr;
+  int a_zp_stride = 0, b_zp_stride = 0;
+  const float* a_scale = nullptr;    // out != 0: scalar
+  const float* b_scale = nullptr;    // scalar or per column
+  int b_scale_stride = 0;
+  const float* y_scale = nullptr;
+  const void* y_zp = nullptr;        // one u8 / s8 (the output type)
+  const int32_t* bias = nullptr;     // [N] per batch entry, or null
+  int64_t stride_n = 0;
+  // conv = 1: A is the implicit im2col of an NHWC u8 / s8 input, as in GemmArgs (trans_b = 1, a_zp scalar:
+  // the padding holds the zero point)
+  int conv = 0;
+  int H = 0, W = 0, C = 0, R = 1, S = 1, stride_h = 1, stride_w = 1, pad_h = 0, pad_w = 0, dil_h = 1, dil_w = 1;
+  int OH = 0, OW = 0;
+};
+int QGemmMfma(const QGemmArgs& g, void* stream);
 // Direct grouped / depthwise NHWC convolution (conv_direct.hip): x [B,H,W,C], w [Cout][R][S][C/groups],
 // y [B,OH,OW,Cout]; fp32 accumulation; y = conv + bias, relu (1: before the residual add, 2: after), + res.
 struct GroupConvArgs {

@@ -25,6 +25,7 @@ arrays for strings, Python lists for sequences, None for empty optionals.
 from __future__ import annotations
 
 import math
+import os
 import re
 from typing import List, Optional
 
@@ -479,6 +480,16 @@ def _dyn_quantize(rt, at, x):
     return [_quantize(xf, sc, z, torch.uint8), sc, z]
 
 
+def _qgemm(a: torch.Tensor, b: torch.Tensor, a_zp, b_zp, group=None):
+    """ops.qgemm (the int8 MFMA kernel) when the operands are on the device and it takes the problem, else
+    None: the operator runs the host path below. SML_QGEMM=0 forces the host path."""
+    if not a.is_cuda or os.environ.get("SML_QGEMM", "1") == "0":
+        return None
+    from ..ops import qgemm
+
+    return qgemm if qgemm.supported(a, b, a_zp, b_zp, group=group) else None
+
+
 def _int_matmul(a: torch.Tensor, b: torch.Tensor, azp, bzp) -> torch.Tensor:
     """(A - a_zp) @ (B - b_zp), exact (fp64 accumulation of integer products); a_zp per row, b_zp per column"""
     af = a.to(torch.float64)
@@ -501,6 +512,9 @@ def _matmul_integer(rt, at, x):
     b = b.to(a.device)
     azp = _t(x[2], a.device) if len(x) > 2 and x[2] is not None else None
     bzp = _t(x[3], a.device) if len(x) > 3 and x[3] is not None else None
+    q = _qgemm(a, b, azp, bzp)
+    if q is not None:
+        return [q.matmul_integer(a, b, azp, bzp)]
     return [_int_matmul(a, b, azp, bzp).to(torch.int32)]
 
 
@@ -521,6 +535,16 @@ def _conv_f64(xf, wf, at, bias=None):
 @op("ConvInteger")
 def _conv_integer(rt, at, x):
     xq, w = _t(x[0]), _t(x[1])
+    if xq.is_cuda:
+        xz = _t(x[2], xq.device) if len(x) > 2 and x[2] is not None else None
+        wzp = _t(x[3], xq.device) if len(x) > 3 and x[3] is not None else None
+        w = w.to(xq.device)
+        q = _qgemm(xq, w, xz, wzp, group=at.get("group", 1))
+        if q is not None:
+            from .ops import conv_args
+
+            _, strides, dil, pb, pe = conv_args(at, xq.shape, w.shape)
+            return [q.conv_integer(xq, w, xz, wzp, strides, list(pb) + list(pe), dil, at.get("group", 1))]
     xf = xq.to(torch.float64)
     wf = w.to(torch.float64).to(xf.device)
     if len(x) > 2 and x[2] is not None:
@@ -529,6 +553,11 @@ def _conv_integer(rt, at, x):
         wz = _t(x[3], xf.device).to(torch.float64)
         wf = wf - (wz.reshape([-1] + [1] * (wf.dim() - 1)) if wz.numel() > 1 else wz.reshape(()))
     return [_conv_f64(xf, wf, at).round().to(torch.int32)]
+
+
+def _qout_ok(y_zp) -> bool:
+    t = _t(y_zp)
+    return t.dtype in (torch.uint8, torch.int8) and t.numel() == 1
 
 
 def _requant(acc: torch.Tensor, mult: torch.Tensor, y_scale, y_zp) -> torch.Tensor:
@@ -546,6 +575,9 @@ def _qlinear_matmul(rt, at, x):
     a = _t(x[0])
     dev = a.device
     a_s, a_z, b, b_s, b_z = (_t(v, dev) for v in x[1:6])
+    q = _qgemm(a, b, a_z, b_z) if _qout_ok(x[7]) else None
+    if q is not None:
+        return [q.qlinear_matmul(a, a_s, a_z, b, b_s, b_z, _t(x[6], dev), _t(x[7], dev))]
     acc = _int_matmul(a, b, a_z, b_z)
     bs = b_s.to(torch.float64)
     mult = a_s.to(torch.float64).reshape(()) * (bs.reshape(1, -1) if bs.numel() > 1 else bs.reshape(()))
@@ -557,6 +589,14 @@ def _qlinear_conv(rt, at, x):
     xq = _t(x[0])
     dev = xq.device
     x_s, x_z, w, w_s, w_z = (_t(v, dev) for v in x[1:6])
+    q = _qgemm(xq, w, x_z, w_z, group=at.get("group", 1)) if _qout_ok(x[7]) else None
+    if q is not None:
+        from .ops import conv_args
+
+        _, strides, dil, pb, pe = conv_args(at, xq.shape, w.shape)
+        bias = _t(x[8], dev) if len(x) > 8 and x[8] is not None else None
+        return [q.qlinear_conv(xq, x_s, x_z, w, w_s, w_z, _t(x[6], dev), _t(x[7], dev), bias, strides,
+                               list(pb) + list(pe), dil, at.get("group", 1))]
     xf = xq.to(torch.float64) - x_z.to(torch.float64).reshape(())
     wf = w.to(torch.float64)
     wz = w_z.to(torch.float64)

@@ -76,13 +76,15 @@ MODULES = {
     ),
     "_nn": (
         "csrc/nn",
-        ["nn_bindings.cpp", "nn_ops.hip", "conv_mfma.hip", "gemm_mfma.hip", "conv_direct.hip"],
+        ["nn_bindings.cpp", "nn_ops.hip", "conv_mfma.hip", "gemm_mfma.hip", "conv_direct.hip", "qgemm_mfma.hip"],
         [],
     ),
 }
 
 CXXFLAGS = ["-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-sign-compare"]
 HOST_DEFS = ["-D__HIP_PLATFORM_AMD__=1", f"-I{ROCM}/include"]
+# per-source hipcc flags: the quantised kernel is built without packed-fp32 instructions
+HIP_EXTRA = {"qgemm_mfma.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _run(cmd: list[str]) -> None:
@@ -105,7 +107,7 @@ def _obj_for(src: Path, flags: list[str]) -> Path:
 def compile_one(src: Path, inc: list[str]) -> Path:
     if src.suffix == ".hip":
         flags = [str(ROCM / "bin" / "hipcc"), f"--offload-arch={ARCH}", "-x", "hip", *CXXFLAGS,
-                 "-munsafe-fp-atomics", *inc]
+                 "-munsafe-fp-atomics", *HIP_EXTRA.get(src.name, []), *inc]
     else:
         flags = ["g++", "-fopenmp", *CXXFLAGS, *HOST_DEFS, *inc]
     obj = _obj_for(src, flags)
