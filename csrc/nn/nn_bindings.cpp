@@ -146,6 +146,28 @@ PYBIND11_MODULE(_nn, m) {
      pybind11::arg("K"), pybind11::arg("batch"), pybind11::arg("lda"), pybind11::arg("ldb"), pybind11::arg("ldc"),
      pybind11::arg("sa"), pybind11::arg("sb"), pybind11::arg("sc"), pybind11::arg("flags"), pybind11::arg("ptrs"),
      pybind11::arg("stride_n"), pybind11::arg("stream"), pybind11::arg("conv") = std::vector<int>());
+  // fused attention (K22). dims: B, heads, S, L, d, causal; strides (elements): q, k, v (batch, row, head)
+  // each, then bias (batch, head, row); key_add / bias: 0 = absent. Returns false when the kernel does not
+  // take the shape (nothing was launched).
+  m.def("attention", [](uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t out, std::vector<int> dims,
+                        std::vector<int64_t> strides, float scale, uintptr_t key_add, uintptr_t bias, int dtype,
+                        uintptr_t stream) {
+    if (dims.size() != 6 || strides.size() != 12) throw std::invalid_argument("attention: 6 dims, 12 strides");
+    AttnArgs a;
+    a.q = P<const void>(q); a.k = P<const void>(k); a.v = P<const void>(v); a.out = P<void>(out);
+    a.B = dims[0]; a.heads = dims[1]; a.S = dims[2]; a.L = dims[3]; a.d = dims[4]; a.causal = dims[5];
+    a.q_sb = strides[0]; a.q_sr = strides[1]; a.q_sh = strides[2];
+    a.k_sb = strides[3]; a.k_sr = strides[4]; a.k_sh = strides[5];
+    a.v_sb = strides[6]; a.v_sr = strides[7]; a.v_sh = strides[8];
+    a.bias_sb = strides[9]; a.bias_sh = strides[10]; a.bias_sr = strides[11];
+    a.scale = scale; a.key_add = P<const float>(key_add); a.bias = P<const float>(bias);
+    const int rc = AttnMfma(a, dtype, P<void>(stream));
+    if (rc == -4) return false;
+    if (rc != 0) throw std::runtime_error("attn_mfma failed (rc=" + std::to_string(rc) + ")");
+    return true;
+  }, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("out"), pybind11::arg("dims"),
+     pybind11::arg("strides"), pybind11::arg("scale"), pybind11::arg("key_add"), pybind11::arg("bias"),
+     pybind11::arg("dtype"), pybind11::arg("stream"));
   m.def("group_conv", [](uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t bias, uintptr_t res, std::vector<int> g,
                          int groups, int relu, int dtype, uintptr_t stream) {
     if (g.size() != 15) throw std::invalid_argument("geometry: B,H,W,C,Cout,R,S,sh,sw,ph,pw,dh,dw,OH,OW");

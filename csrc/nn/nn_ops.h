@@ -115,6 +115,30 @@ struct QGemmArgs {
   int OH = 0, OW = 0;
 };
 int QGemmMfma(const QGemmArgs& g, void* stream);
+// K22: fused online-softmax attention forward on the f16 / bf16 MFMA (attn_mfma.hip), dtype 1 fp16 / 2 bf16:
+//   out[b, s, h, :] = softmax_l(scale * q[b,s,h,:] . k[b,l,h,:] + key_add[b,l] + bias[b,h,s,l] + causal(s,l))
+//                     . v[b,l,h,:]
+// q [B, S, heads, d], k / v [B, L, heads, d] are read through element strides (batch, row, head; unit stride
+// along d; pointers 16-byte aligned, strides multiples of 8); out is [B, S, heads * d] contiguous in the
+// input dtype. d is 32, 64 or 128. causal: key l is visible to query s iff l <= s + (L - S) (needs L >= S).
+// Returns 0, or < 0 when the shape is not supported (-4: head size, causal with L < S, B or heads > 65535,
+// misaligned operands).
+struct AttnArgs {
+  const void* q = nullptr;
+  const void* k = nullptr;
+  const void* v = nullptr;
+  void* out = nullptr;
+  int B = 0, heads = 0, S = 0, L = 0, d = 0;
+  int64_t q_sb = 0, q_sr = 0, q_sh = 0;
+  int64_t k_sb = 0, k_sr = 0, k_sh = 0;
+  int64_t v_sb = 0, v_sr = 0, v_sh = 0;
+  float scale = 1.f;               // applied to the fp32 scores before the additive terms
+  const float* key_add = nullptr;  // [B][L] added to every query row, or null
+  const float* bias = nullptr;     // element (b, h, s, l) at b * bias_sb + h * bias_sh + s * bias_sr + l, or null
+  int64_t bias_sb = 0, bias_sh = 0, bias_sr = 0;  // 0 = broadcast
+  int causal = 0;
+};
+int AttnMfma(const AttnArgs& a, int dtype, void* stream);
 // Direct grouped / depthwise NHWC convolution (conv_direct.hip): x [B,H,W,C], w [Cout][R][S][C/groups],
 // y [B,OH,OW,Cout]; fp32 accumulation; y = conv + bias, relu (1: before the residual add, 2: after), + res.
 struct GroupConvArgs {

@@ -1197,6 +1197,36 @@ def _mask_to_add(mask, B, S, L, dev, filt: float):
     raise NotImplementedError(f"attention mask of shape {tuple(m.shape)}")
 
 
+def _attend_fused(q, k, v, heads: int, scale: Optional[float], mask, rb, filt: float, causal: bool):
+    """ops.attention (the fused MFMA kernel, K22) when the operands are on the device and it takes the problem,
+    else None: the operator runs _attend(). 1-D / 2-D masks become the kernel's fp32 [B, L] key term, a 3-D
+    mask and the relative position bias its broadcast bias. SML_ATTN=0 forces _attend()."""
+    if not q.is_cuda or os.environ.get("SML_ATTN", "1") == "0":
+        return None
+    from ..ops import attention as fused
+
+    if not fused.supported(q, k, v, heads, causal=causal):
+        return None
+    B, S, L, dev = q.shape[0], q.shape[1], k.shape[1], q.device
+    key_add = bias = None
+    if mask is not None:
+        m = _t(mask, dev)
+        if m.dim() == 1 and m.numel() == B:
+            keep = torch.arange(L, device=dev).unsqueeze(0) < m.reshape(B, 1).to(torch.long)
+            key_add = torch.where(keep, 0.0, filt)
+        elif m.dim() == 2:
+            key_add = torch.where(m.to(torch.bool), 0.0, filt).reshape(B, L)
+        elif m.dim() == 3:
+            bias = torch.where(m.to(torch.bool), 0.0, filt).reshape(B, 1, S, L)
+        else:
+            return None
+    if rb is not None:
+        bias = rb if bias is None else bias + rb
+    if not fused.supported(q, k, v, heads, key_add, bias, causal):
+        return None
+    return fused.attention(q, k, v, heads, scale, key_add, bias, causal)
+
+
 @op("Attention")
 def _attention(rt, at, x):
     xs = list(x) + [None] * (8 - len(x))
@@ -1220,11 +1250,14 @@ def _attention(rt, at, x):
     if rt.node_num_outputs > 1:
         present = torch.stack([k.reshape(B, L, heads, -1).transpose(1, 2), v.reshape(B, L, heads, -1).transpose(1, 2)])
     filt = float(at.get("mask_filter_value", -10000.0))
-    mask_add = _mask_to_add(xs[3], B, S, L, dev, filt)
-    if xs[5] is not None:  # relative position bias [B|1, heads, S, L]
-        rb = _t(xs[5], dev, torch.float32)
-        mask_add = rb if mask_add is None else mask_add + rb
-    out = _attend(q, k, v, heads, at.get("scale"), mask_add, bool(int(at.get("unidirectional", 0))))
+    causal = bool(int(at.get("unidirectional", 0)))
+    rb = _t(xs[5], dev, torch.float32) if xs[5] is not None else None  # relative position bias [B|1, heads, S, L]
+    out = _attend_fused(q, k, v, heads, at.get("scale"), xs[3], rb, filt, causal)
+    if out is None:
+        mask_add = _mask_to_add(xs[3], B, S, L, dev, filt)
+        if rb is not None:
+            mask_add = rb if mask_add is None else mask_add + rb
+        out = _attend(q, k, v, heads, at.get("scale"), mask_add, causal)
     return [out, present][:max(1, rt.node_num_outputs)]
 
 
@@ -1239,9 +1272,13 @@ def _mha(rt, at, x):
         D, Dv = q.shape[-1], v.shape[-1]
         q, k, v = q + b[:D], k + b[D:2 * D], v + b[2 * D:2 * D + Dv]
     B, S, L = q.shape[0], q.shape[1], k.shape[1]
-    mask_add = _mask_to_add(xs[4], B, S, L, dev, float(at.get("mask_filter_value", -10000.0)))
-    if xs[5] is not None:
-        rb = _t(xs[5], dev, torch.float32)
-        mask_add = rb if mask_add is None else mask_add + rb
-    out = _attend(q, k, v, int(at["num_heads"]), at.get("scale"), mask_add, bool(int(at.get("unidirectional", 0))))
+    heads, filt = int(at["num_heads"]), float(at.get("mask_filter_value", -10000.0))
+    causal = bool(int(at.get("unidirectional", 0)))
+    rb = _t(xs[5], dev, torch.float32) if xs[5] is not None else None
+    out = _attend_fused(q, k, v, heads, at.get("scale"), xs[4], rb, filt, causal)
+    if out is None:
+        mask_add = _mask_to_add(xs[4], B, S, L, dev, filt)
+        if rb is not None:
+            mask_add = rb if mask_add is None else mask_add + rb
+        out = _attend(q, k, v, heads, at.get("scale"), mask_add, causal)
     return [out]
