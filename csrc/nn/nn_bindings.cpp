@@ -168,6 +168,27 @@ PYBIND11_MODULE(_nn, m) {
   }, pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("out"), pybind11::arg("dims"),
      pybind11::arg("strides"), pybind11::arg("scale"), pybind11::arg("key_add"), pybind11::arg("bias"),
      pybind11::arg("dtype"), pybind11::arg("stream"));
+  // fused top-k inner-product search (K23). dims: M, N, D, k, W (allow words per query), splits (0: planned);
+  // pitches (floats): q, keys; key_label / allow / ws: 0 = absent (ws: uint64 [splits][M][k], needed when
+  // splits != 1). Returns false when the kernel does not take the shape (nothing was launched).
+  m.def("mips_topk", [](uintptr_t q, uintptr_t keys, uintptr_t vals, uintptr_t idx, std::vector<int> dims,
+                        std::vector<int64_t> pitches, uintptr_t key_label, uintptr_t allow, uintptr_t ws,
+                        uintptr_t stream) {
+    if (dims.size() != 6 || pitches.size() != 2) throw std::invalid_argument("mips_topk: 6 dims, 2 pitches");
+    MipsArgs a;
+    a.q = P<const float>(q); a.keys = P<const float>(keys); a.vals = P<float>(vals); a.idx = P<int32_t>(idx);
+    a.M = dims[0]; a.N = dims[1]; a.D = dims[2]; a.k = dims[3]; a.W = dims[4]; a.splits = dims[5];
+    a.q_pitch = pitches[0]; a.k_pitch = pitches[1];
+    a.key_label = P<const int32_t>(key_label); a.allow = P<const uint32_t>(allow); a.ws = P<uint64_t>(ws);
+    const int rc = MipsTopk(a, P<void>(stream));
+    if (rc == -4) return false;
+    if (rc != 0) throw std::runtime_error("mips_topk failed (rc=" + std::to_string(rc) + ")");
+    return true;
+  }, pybind11::arg("q"), pybind11::arg("keys"), pybind11::arg("vals"), pybind11::arg("idx"), pybind11::arg("dims"),
+     pybind11::arg("pitches"), pybind11::arg("key_label"), pybind11::arg("allow"), pybind11::arg("ws"),
+     pybind11::arg("stream"));
+  m.def("mips_split_plan", &MipsSplitPlan);
+  m.attr("MIPS_MAX_LABELS") = kMipsMaxLabels;
   m.def("group_conv", [](uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t bias, uintptr_t res, std::vector<int> g,
                          int groups, int relu, int dtype, uintptr_t stream) {
     if (g.size() != 15) throw std::invalid_argument("geometry: B,H,W,C,Cout,R,S,sh,sw,ph,pw,dh,dw,OH,OW");

@@ -139,6 +139,32 @@ struct AttnArgs {
   int causal = 0;
 };
 int AttnMfma(const AttnArgs& a, int dtype, void* stream);
+// K23: fused top-k maximum-inner-product search on the fp32 MFMA (mips_topk.hip): per query row of q [M, D] the
+// k largest q[m, :] . keys[n, :] over keys [N, D], descending, ties by the smaller n; vals fp32 [M, k], idx
+// int32 [M, k], slots that cannot be filled hold -inf / -1. Rows have unit stride along D and pitches in
+// floats (multiples of 4, readable up to D rounded up to 4; pointers 16-byte aligned). Optional conditioner:
+// key_label int32 [N] (dense label ids) and allow uint32 [M, W] (bit l of row m set: label l is eligible for
+// query m; a label outside [0, 32 W) is never eligible); both null or both set. splits > 1 spreads the keys
+// of a query tile over that many blocks through ws (uint64 [splits][M][k]); 0 takes MipsSplitPlan. Every
+// value is read on the device. Returns 0, or < 0 when not supported (-4: k > 64, W > kMipsMaxLabels / 32,
+// N > 2^31 - 256, pitches or alignment the 16-byte loads cannot read).
+constexpr int kMipsMaxLabels = 2048;
+struct MipsArgs {
+  const float* q = nullptr;
+  const float* keys = nullptr;
+  float* vals = nullptr;
+  int32_t* idx = nullptr;
+  int M = 0, N = 0, D = 0, k = 0;
+  int64_t q_pitch = 0, k_pitch = 0;
+  const int32_t* key_label = nullptr;
+  const uint32_t* allow = nullptr;
+  int W = 0;
+  int splits = 0;
+  uint64_t* ws = nullptr;
+};
+// key splits the shapes and the CU count suggest (1: the query tiles fill the device on their own)
+int MipsSplitPlan(int M, int N, int k, int conditioned);
+int MipsTopk(const MipsArgs& a, void* stream);
 // Direct grouped / depthwise NHWC convolution (conv_direct.hip): x [B,H,W,C], w [Cout][R][S][C/groups],
 // y [B,OH,OW,Cout]; fp32 accumulation; y = conv + bias, relu (1: before the residual add, 2: after), + res.
 struct GroupConvArgs {

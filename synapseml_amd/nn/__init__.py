@@ -3,12 +3,18 @@
 
 ``BallTree`` / ``ConditionalBallTree`` reproduce the reference's exact
 branch-and-bound search on the host. ``KNNModel.transform`` is exact MIPS as
-a blocked GEMM (queries × keysᵀ) + top-k on the device when a GPU is visible
-— on the MI355X a dense GEMM over all keys beats tree traversal — and falls
-back to the ball tree on the host."""
+a dense scan of all keys on the device when a GPU is visible — on the MI355X
+that beats tree traversal — and falls back to the ball tree on the host. The
+device scan is the fused MFMA top-k kernel (K23, ``ops.mips``): scores stay in
+registers, the conditioner is a label id per key and a bitset per query, and
+the fp32 keys are uploaded once per tree. ``k`` > 64, more than
+``ops.mips.MAX_LABELS`` labels, unconditional keys wider than 512, non-finite
+data or ``SML_MIPS=0`` take the blocked GEMM + ``torch.topk`` path
+(``_device_mips``) instead."""
 from __future__ import annotations
 
 import heapq
+import os
 from typing import Any, Dict, List, Optional, Sequence, Set
 
 import numpy as np
@@ -46,6 +52,10 @@ class BallTree:
         self.values = list(values)
         self.leaf_size = leafSize
         self.root = self._build(np.arange(len(self.keys)))
+
+    def __getstate__(self):
+        # the device copy of the keys (_device_topk) is rebuilt on demand, never pickled or saved
+        return {k: v for k, v in self.__dict__.items() if k != "_dev"}
 
     def _build(self, idx: np.ndarray) -> _Node:
         pts = self.keys[idx]
@@ -140,6 +150,76 @@ def _device_mips(Q: np.ndarray, K: np.ndarray, k: int, mask: Optional[np.ndarray
     return np.concatenate(out_v), np.concatenate(out_i)
 
 
+# Widest unconditional keys the fused kernel serves: at D = 2048 it was slower than the torch path's device steps
+# at every measured shape, at D = 128 faster wherever the queries fill the device (profiles/r9/mips); nothing was
+# measured in between. The conditional stage always takes the kernel: its torch path builds a Q x N mask on
+# the host, which costs more than either device path.
+_MIPS_MAX_D = 512
+
+
+def _device_keys(bt: "BallTree", conditional: bool):
+    """The tree's device-side operands, cached on the tree per device: fp32 keys, whether they are finite and,
+    for a conditional tree, the dense label ids (dict label -> id, int32 id per key)"""
+    import torch
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    cache = bt.__dict__.setdefault("_dev", {})
+    ent = cache.get(dev)
+    if ent is None:
+        ent = {"keys": torch.as_tensor(bt.keys, dtype=torch.float32, device=dev),
+               "finite": bool(np.isfinite(bt.keys).all())}
+        cache[dev] = ent
+    if conditional and "ids" not in ent:
+        ids: Dict[Any, int] = {}
+        for l in bt.labels:
+            ids.setdefault(l, len(ids))
+        ent["ids"] = ids
+        ent["key_label"] = torch.as_tensor(np.fromiter((ids[l] for l in bt.labels), np.int32, len(bt.labels)),
+                                           device=dev)
+    return ent
+
+
+def _device_topk(bt: "BallTree", Q: np.ndarray, k: int, conds: Optional[List[Set[Any]]] = None, block: int = 8192):
+    """Top-k inner products of every query against the tree's keys on the device: (vals, idx) with -inf / -1 in
+    the slots that cannot be filled, from the fused kernel (ops.mips); None when the kernel does not take the
+    problem (the caller then runs ``_device_mips``)."""
+    if os.environ.get("SML_MIPS", "1") == "0" or not 1 <= k <= 64 or not len(bt.keys):
+        return None
+    if conds is None and bt.keys.shape[1] > _MIPS_MAX_D:
+        return None
+    import torch
+
+    from ..ops import mips
+
+    ent = _device_keys(bt, conds is not None)
+    if not ent["finite"] or not np.isfinite(Q).all():
+        return None
+    words = 0
+    if conds is not None:
+        if len(ent["ids"]) > mips.MAX_LABELS:
+            return None
+        words = mips.allow_words(len(ent["ids"]))
+    out_v, out_i = [], []
+    for s in range(0, len(Q), block):
+        q = torch.as_tensor(Q[s:s + block], dtype=torch.float32, device=ent["keys"].device)
+        key_label = allow = None
+        if conds is not None:
+            bits = np.zeros((len(q), words), np.uint32)
+            ids = ent["ids"]
+            for r, c in enumerate(conds[s:s + block]):
+                for l in c:
+                    i = ids.get(l)
+                    if i is not None:
+                        bits[r, i >> 5] |= np.uint32(1 << (i & 31))
+            key_label, allow = ent["key_label"], torch.as_tensor(bits.view(np.int32), device=q.device)
+        if not mips.supported(q, ent["keys"], k, key_label, allow):
+            return None
+        v, i = mips.topk(q, ent["keys"], k, key_label, allow)
+        out_v.append(v.cpu().numpy())
+        out_i.append(i.cpu().numpy())
+    return np.concatenate(out_v), np.concatenate(out_i)
+
+
 def _use_gpu() -> bool:
     try:
         import torch
@@ -172,9 +252,11 @@ class KNNModel(Model, _KNNParams):
         k = self.getK()
         res = []
         if _use_gpu() and len(Q):
-            vals, idx = _device_mips(Q, bt.keys, k)
+            fused = _device_topk(bt, Q, k)
+            vals, idx = fused if fused is not None else _device_mips(Q, bt.keys, k)
             for r in range(len(Q)):
-                res.append([{"value": bt.values[int(i)], "distance": float(v)} for v, i in zip(vals[r], idx[r])])
+                res.append([{"value": bt.values[int(i)], "distance": float(v)} for v, i in zip(vals[r], idx[r])
+                            if i >= 0])
         else:
             for q in Q:
                 res.append([{"value": bt.values[m.index], "distance": m.distance}
@@ -205,7 +287,13 @@ class ConditionalKNNModel(Model, _KNNParams, HasLabelCol):
         conds = [set(c) for c in df[self.getConditionerCol()].tolist()]
         k = self.getK()
         res = []
-        if _use_gpu() and len(Q):
+        fused = _device_topk(bt, Q, k, conds) if _use_gpu() and len(Q) else None
+        if fused is not None:
+            vals, idx = fused
+            for r in range(len(Q)):
+                res.append([{"value": bt.values[int(i)], "distance": float(v), "label": bt.labels[int(i)]}
+                            for v, i in zip(vals[r], idx[r]) if i >= 0])
+        elif _use_gpu() and len(Q):
             labels = np.asarray(bt.labels, dtype=object)
             mask = np.stack([np.asarray([l in c for l in labels]) for c in conds])
             vals, idx = _device_mips(Q, bt.keys, k, mask)
