@@ -189,6 +189,23 @@ PYBIND11_MODULE(_nn, m) {
      pybind11::arg("stream"));
   m.def("mips_split_plan", &MipsSplitPlan);
   m.attr("MIPS_MAX_LABELS") = kMipsMaxLabels;
+  // fused persistent LSTM / GRU (K24). ptrs: xw, r, h0, c0, peep, rbh, lens, y, yh, yc (0 = absent); dims: cell
+  // (0 LSTM, 1 GRU), T, N, H, nd, reverse bits, linear_before_reset, coupled. Returns false when the kernel
+  // does not take the shape (nothing was launched).
+  m.def("rnn", [](std::vector<uintptr_t> ptrs, std::vector<int> dims, float clip, uintptr_t stream) {
+    if (ptrs.size() != 10 || dims.size() != 8) throw std::invalid_argument("rnn: 10 pointers, 8 dims");
+    RnnArgs a;
+    a.xw = P<const float>(ptrs[0]); a.r = P<const float>(ptrs[1]); a.h0 = P<const float>(ptrs[2]);
+    a.c0 = P<const float>(ptrs[3]); a.peep = P<const float>(ptrs[4]); a.rbh = P<const float>(ptrs[5]);
+    a.lens = P<const int32_t>(ptrs[6]); a.y = P<float>(ptrs[7]); a.yh = P<float>(ptrs[8]); a.yc = P<float>(ptrs[9]);
+    a.cell = dims[0]; a.T = dims[1]; a.N = dims[2]; a.H = dims[3]; a.nd = dims[4]; a.reverse = dims[5];
+    a.linear_before_reset = dims[6]; a.coupled = dims[7];
+    a.clip = clip;
+    const int rc = RnnMfma(a, P<void>(stream));
+    if (rc == -4) return false;
+    if (rc != 0) throw std::runtime_error("rnn_mfma failed (rc=" + std::to_string(rc) + ")");
+    return true;
+  }, pybind11::arg("ptrs"), pybind11::arg("dims"), pybind11::arg("clip"), pybind11::arg("stream"));
   m.def("group_conv", [](uintptr_t x, uintptr_t w, uintptr_t y, uintptr_t bias, uintptr_t res, std::vector<int> g,
                          int groups, int relu, int dtype, uintptr_t stream) {
     if (g.size() != 15) throw std::invalid_argument("geometry: B,H,W,C,Cout,R,S,sh,sw,ph,pw,dh,dw,OH,OW");

@@ -165,6 +165,38 @@ struct MipsArgs {
 // key splits the shapes and the CU count suggest (1: the query tiles fill the device on their own)
 int MipsSplitPlan(int M, int N, int k, int conditioned);
 int MipsTopk(const MipsArgs& a, void* stream);
+// K24: fused persistent LSTM / GRU on the fp32 MFMA (rnn_mfma.hip): one launch runs all T steps of every
+// direction with the state of a 16-item batch tile on chip. Default activations (Sigmoid, Tanh), fp32.
+//   xw   [nd][T][N][gates * Hp]: the input projection with Wb and every part of Rb that is added before an
+//        activation (LSTM: all of it; GRU: Rbz, Rbr, and Rbh when linear_before_reset = 0), each gate padded
+//        with zeros to Hp = H rounded up to 16. Gates: LSTM i, o, f, c; GRU z, r, h.
+//   r    [nd][Hp / 16 unit tiles][gates][Hp / 16 k chunks][64 lanes][4]: value (lane, j) is
+//        R[gate * H + 16 tile + lane % 16][16 chunk + 4 (lane / 16) + j], zero past H
+//   h0, c0 [nd][N][H] or null (zeros); peep [nd][3][Hp] (i, o, f; zero-padded) or null; rbh [nd][Hp] or null
+//   (GRU, linear_before_reset = 1); lens int32 [N] or null (every item runs T steps; values are clamped to
+//   [0, T]); y [T][nd][N][H] (every element is written), yh [nd][N][H], yc [nd][N][H] or null.
+// Bit d of reverse: direction d walks time backwards from its length. clip 0: none. xw, r, peep, rbh are
+// 16-byte aligned, y / yh / yc too when H % 4 == 0. Every value is read on the device. Returns 0, or < 0 when
+// not supported (-4: H > 512, nd > 2, an empty dimension, a negative clip, misaligned operands).
+struct RnnArgs {
+  int cell = 0;  // 0 LSTM, 1 GRU
+  const float* xw = nullptr;
+  const float* r = nullptr;
+  const float* h0 = nullptr;
+  const float* c0 = nullptr;
+  const float* peep = nullptr;
+  const float* rbh = nullptr;
+  const int32_t* lens = nullptr;
+  float* y = nullptr;
+  float* yh = nullptr;
+  float* yc = nullptr;
+  int T = 0, N = 0, H = 0, nd = 1;
+  int reverse = 0;
+  float clip = 0.f;
+  int linear_before_reset = 0;  // GRU
+  int coupled = 0;              // LSTM input_forget: f = 1 - i
+};
+int RnnMfma(const RnnArgs& a, void* stream);
 // Direct grouped / depthwise NHWC convolution (conv_direct.hip): x [B,H,W,C], w [Cout][R][S][C/groups],
 // y [B,OH,OW,Cout]; fp32 accumulation; y = conv + bias, relu (1: before the residual add, 2: after), + res.
 struct GroupConvArgs {

@@ -312,8 +312,44 @@ def _init_state(x, i, nd, N, H, dev, dt, layout):
     return torch.zeros(nd, N, H, device=dev, dtype=dt)
 
 
+def _rnn_fused(rt, at, x, gates: int):
+    """LSTM (gates = 4) / GRU (gates = 3) on ops.rnn (the fused persistent MFMA kernel, K24) when X is on the
+    device, the activations are the defaults and the kernel takes the problem, else None: the operator runs the
+    time loop below. Nothing is read on the host. SML_RNN=0 forces the time loop."""
+    if not (isinstance(x[0], torch.Tensor) and x[0].is_cuda) or os.environ.get("SML_RNN", "1") == "0":
+        return None
+    from ..ops import rnn as fused
+
+    names = [a.decode() if isinstance(a, bytes) else a for a in at.get("activations", [])]
+    layout, dev = int(at.get("layout", 0)), x[0].device
+    arg = [None if len(x) <= i or x[i] is None else _t(x[i], dev) for i in range(8)]
+    X, W, R, B, lens = arg[:5]
+    if W.dim() != 3 or [n.lower() for n in names] not in ([], (["sigmoid", "tanh", "tanh"][:gates - 1]) * W.shape[0]):
+        return None
+    if layout:
+        X = X.transpose(0, 1)
+    states = [s.transpose(0, 1) if layout and s is not None and s.dim() == 3 else s for s in arg[5:gates + 3]]
+    direction = at.get("direction", "forward")
+    direction = direction.decode() if isinstance(direction, bytes) else direction
+    if W.shape[0] == 2:
+        direction = "bidirectional"
+    clip = at.get("clip")
+    if not fused.supported(X, W, R, gates, B, lens, tuple(states), arg[7], direction, clip):
+        return None
+    if gates == 4:
+        outs = fused.lstm(X, W, R, B, lens, states[0], states[1], arg[7], direction, clip,
+                          bool(int(at.get("input_forget", 0))))
+    else:
+        outs = fused.gru(X, W, R, B, lens, states[0], direction, clip, bool(int(at.get("linear_before_reset", 0))))
+    outs = [outs[0].permute(2, 0, 1, 3) if layout else outs[0]] + [o.transpose(0, 1) if layout else o for o in outs[1:]]
+    return outs[:max(1, rt.node_num_outputs)]
+
+
 @op("LSTM")
 def _lstm(rt, at, x):
+    fused = _rnn_fused(rt, at, x, 4)
+    if fused is not None:
+        return fused
     layout, X, W, R, B, nd, H, T, N, lens, direction, clip, dev, dt = _rnn_common(at, x, 4)
     h0 = _init_state(x, 5, nd, N, H, dev, dt, layout)
     c0 = _init_state(x, 6, nd, N, H, dev, dt, layout)
@@ -368,6 +404,9 @@ def _run_lstm(step, XW, nd, direction, T, N, H, lens, init, dev, dt):
 
 @op("GRU")
 def _gru(rt, at, x):
+    fused = _rnn_fused(rt, at, x, 3)
+    if fused is not None:
+        return fused
     layout, X, W, R, B, nd, H, T, N, lens, direction, clip, dev, dt = _rnn_common(at, x, 3)
     h0 = _init_state(x, 5, nd, N, H, dev, dt, layout)
     acts = _acts(at, ["Sigmoid", "Tanh"], nd)

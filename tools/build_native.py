@@ -77,16 +77,18 @@ MODULES = {
     "_nn": (
         "csrc/nn",
         ["nn_bindings.cpp", "nn_ops.hip", "conv_mfma.hip", "gemm_mfma.hip", "conv_direct.hip", "qgemm_mfma.hip",
-         "attn_mfma.hip", "mips_topk.hip"],
+         "attn_mfma.hip", "mips_topk.hip", "rnn_mfma.hip"],
         [],
     ),
 }
 
 CXXFLAGS = ["-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-sign-compare"]
 HOST_DEFS = ["-D__HIP_PLATFORM_AMD__=1", f"-I{ROCM}/include"]
-# per-source hipcc flags: the quantised, attention and top-k kernels are built without packed-fp32 instructions
+# per-source hipcc flags: the quantised, attention, top-k and recurrent kernels are built without packed-fp32
+# instructions
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-HIP_EXTRA = {"qgemm_mfma.hip": _NO_PK_F32, "attn_mfma.hip": _NO_PK_F32, "mips_topk.hip": _NO_PK_F32}
+HIP_EXTRA = {"qgemm_mfma.hip": _NO_PK_F32, "attn_mfma.hip": _NO_PK_F32, "mips_topk.hip": _NO_PK_F32,
+             "rnn_mfma.hip": _NO_PK_F32}
 
 
 def _run(cmd: list[str]) -> None:
