@@ -55,6 +55,9 @@ __device__ __forceinline__ float act_fn(float x, int act, float alpha) {
   return x;
 }
 
+// max that propagates NaN (torch / ONNX Runtime semantics; fmaxf drops it). Bitwise fmaxf on finite / inf inputs.
+__device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }
+
 // channel of element i
 __device__ __forceinline__ int chan(int64_t i, int C, int HW, int nhwc) {
   return nhwc ? static_cast<int>(i % C) : static_cast<int>((i / HW) % C);
@@ -186,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void maxpool_nhwc_kernel(const T* __restr
         for (int k = 0; k < KW; ++k) {
           if (h0 + i < 0 || h0 + i >= H || w0 + k < 0 || w0 + k >= W) continue;
 #pragma unroll
-          for (int j = 0; j < kVec; ++j) m[j] = fmaxf(m[j], ld<T>(v[i][k].v, j));
+          for (int j = 0; j < kVec; ++j) m[j] = max_nan(m[j], ld<T>(v[i][k].v, j));
         }
     }
     for (int i = 0; i < (KH > 0 ? 0 : kh); ++i) {
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void maxpool_nhwc_kernel(const T* __restr
         const Vec8<T> v = *reinterpret_cast<const Vec8<T>*>(x + ((static_cast<int64_t>(n) * H + hh) * W + ww) * C +
                                                            cg * kVec);
 #pragma unroll
-        for (int j = 0; j < kVec; ++j) m[j] = fmaxf(m[j], ld<T>(v.v, j));
+        for (int j = 0; j < kVec; ++j) m[j] = max_nan(m[j], ld<T>(v.v, j));
       }
     }
     if (shift) {
@@ -207,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void maxpool_nhwc_kernel(const T* __restr
     }
     if (relu) {
 #pragma unroll
-      for (int j = 0; j < kVec; ++j) m[j] = fmaxf(m[j], 0.f);
+      for (int j = 0; j < kVec; ++j) m[j] = max_nan(0.f, m[j]);
     }
     Vec8<T> o;
 #pragma unroll
@@ -216,7 +219,8 @@ __global__ __launch_bounds__(kThreads) void maxpool_nhwc_kernel(const T* __restr
   }
 }
 
-// row softmax / argmax, one wave per row (fp32)
+// row softmax / argmax, one wave per row (fp32). Ties go to the lowest index; a NaN beats every number
+// (the first NaN of a row is its argmax, as numpy / torch), and the row's softmax is then all NaN.
 __global__ __launch_bounds__(kThreads) void softmax_rows_kernel(const float* __restrict__ x, int rows, int cols,
                                                                 float* __restrict__ y, int64_t* __restrict__ amax) {
   const int lane = threadIdx.x & 63;
@@ -227,13 +231,15 @@ __global__ __launch_bounds__(kThreads) void softmax_rows_kernel(const float* __r
   int mi = 0x7fffffff;
   for (int j = lane; j < cols; j += 64) {
     const float v = p[j];
-    if (v > m || (v == m && j < mi)) { m = v; mi = j; }
+    const bool vn = v != v, mn = m != m;
+    if (mn ? (vn && j < mi) : (vn || v > m || (v == m && j < mi))) { m = v; mi = j; }
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const float om = __shfl_xor(m, off, 64);
     const int oi = __shfl_xor(mi, off, 64);
-    if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+    const bool on = om != om, mn = m != m;
+    if (mn ? (on && oi < mi) : (on || om > m || (om == m && oi < mi))) { m = om; mi = oi; }
   }
   if (amax && lane == 0) amax[r] = mi;
   if (!y) return;

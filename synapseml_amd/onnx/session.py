@@ -728,7 +728,7 @@ def _stream(t: torch.Tensor) -> int:
 
 
 def _affine_act_torch(x, scale, shift, res, act, alpha):
-    shp = [1, -1] + [1] * (x.dim() - 2)
+    shp = [1, -1] + [1] * (x.dim() - 2) if x.dim() >= 2 else [-1]  # no channel axis below 2-D: plain broadcast
     y = x.float()
     if scale is not None:
         y = y * scale.reshape(shp).float()
@@ -749,10 +749,14 @@ def _affine_act_torch(x, scale, shift, res, act, alpha):
 
 def _affine_act(rt, x, scale, shift, res, act, alpha, out=None):
     nn = rt.session._nn
-    if nn is not None and _kernel_ok(x, res) and x.dim() >= 2:
+    if nn is not None and _kernel_ok(x, res) and x.dim() >= 2 and (res is None or res.dtype == x.dtype):
         lay = _layout(x)
-        if res is not None and (res.shape != x.shape or _layout(res) != lay):
+        if res is not None and lay is not None and (res.shape != x.shape or _layout(res) != lay):
+            # the kernel reads one residual element per element of x: a broadcast residual is expanded first
+            res = res.expand(x.shape) if res.shape != x.shape else res
             res = res.contiguous(memory_format=torch.channels_last) if lay == 1 else res.contiguous()
+            if res.data_ptr() % 16 != 0:
+                lay = None
         if lay is not None:
             y = out if out is not None else torch.empty_like(x)
             C = x.shape[1]
@@ -981,7 +985,7 @@ def _fused_add_affine_act(rt, at, x):
     a, b = (a, b.to(a.dtype)) if a.dtype == b.dtype or not b.is_floating_point() else (a, b.to(a.dtype))
     act = at.get("__act", 0)
     nn = rt.session._nn
-    if nn is not None and a.shape == b.shape and _kernel_ok(a, b):
+    if nn is not None and a.dim() >= 2 and a.shape == b.shape and _kernel_ok(a, b):
         lay = _layout(a)
         if _layout(b) != lay:
             b = b.contiguous(memory_format=torch.channels_last) if lay == 1 else b.contiguous()
