@@ -2,6 +2,8 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -215,6 +217,45 @@ PYBIND11_MODULE(_nn, m) {
     const int rc = GroupConv(a, dtype, P<void>(stream));
     if (rc != 0) throw std::runtime_error("group_conv failed (rc=" + std::to_string(rc) + ")");
   });
+  // fused row normalisation (K25). ptrs (0 = absent): x, skip, bias, gamma, beta, y, sum, mean, inv, ids,
+  // pos_ids, seg_ids, word, pos, seg. dims: rows, N, x row pitch, skip row pitch, skip rows, rms, ids64, S,
+  // word / pos / seg table rows, dtype, bias / gamma / beta dtype. Returns false when the kernel does not take
+  // the problem (nothing was launched).
+  m.def("norm_rows", [](std::vector<uintptr_t> ptrs, std::vector<int64_t> dims, float eps, uintptr_t stream) {
+    if (ptrs.size() != 15 || dims.size() != 15) throw std::invalid_argument("norm_rows: 15 ptrs, 15 dims");
+    NormRowsArgs a;
+    a.x = P<const void>(ptrs[0]); a.skip = P<const void>(ptrs[1]); a.bias = P<const void>(ptrs[2]);
+    a.gamma = P<const void>(ptrs[3]); a.beta = P<const void>(ptrs[4]); a.y = P<void>(ptrs[5]);
+    a.sum = P<void>(ptrs[6]); a.mean = P<float>(ptrs[7]); a.inv = P<float>(ptrs[8]);
+    a.ids = P<const void>(ptrs[9]); a.pos_ids = P<const void>(ptrs[10]); a.seg_ids = P<const void>(ptrs[11]);
+    a.word = P<const void>(ptrs[12]); a.pos = P<const void>(ptrs[13]); a.seg = P<const void>(ptrs[14]);
+    for (size_t i = 4; i < dims.size(); ++i)
+      if (dims[i] < 0 || dims[i] > INT32_MAX) return false;
+    a.rows = dims[0]; a.N = static_cast<int>(std::min<int64_t>(dims[1], INT32_MAX));
+    a.x_rs = dims[2]; a.skip_rs = dims[3]; a.skip_rows = dims[4];
+    a.rms = static_cast<int>(dims[5]); a.ids64 = static_cast<int>(dims[6]); a.S = static_cast<int>(dims[7]);
+    a.word_rows = static_cast<int>(dims[8]); a.pos_rows = static_cast<int>(dims[9]);
+    a.seg_rows = static_cast<int>(dims[10]);
+    a.bias_dt = static_cast<int>(dims[12]); a.gamma_dt = static_cast<int>(dims[13]);
+    a.beta_dt = static_cast<int>(dims[14]); a.eps = eps;
+    const int rc = NormRows(a, static_cast<int>(dims[11]), P<void>(stream));
+    if (rc == -4) return false;
+    if (rc != 0) throw std::runtime_error("norm_rows failed (rc=" + std::to_string(rc) + ")");
+    return true;
+  }, pybind11::arg("ptrs"), pybind11::arg("dims"), pybind11::arg("eps"), pybind11::arg("stream"));
+  // y = act(x + bias) (K25). dims: rows, N, x row pitch, mode, dtype, bias dtype
+  m.def("bias_act", [](uintptr_t x, uintptr_t bias, uintptr_t y, std::vector<int64_t> dims, float alpha,
+                       uintptr_t stream) {
+    if (dims.size() != 6) throw std::invalid_argument("bias_act: 6 dims");
+    if (dims[1] > INT32_MAX) return false;
+    const int rc = BiasAct(P<const void>(x), dims[2], P<const void>(bias), static_cast<int>(dims[5]), P<void>(y),
+                           dims[0], static_cast<int>(dims[1]), static_cast<int>(dims[3]), alpha,
+                           static_cast<int>(dims[4]), P<void>(stream));
+    if (rc == -4) return false;
+    if (rc != 0) throw std::runtime_error("bias_act failed (rc=" + std::to_string(rc) + ")");
+    return true;
+  }, pybind11::arg("x"), pybind11::arg("bias"), pybind11::arg("y"), pybind11::arg("dims"), pybind11::arg("alpha"),
+     pybind11::arg("stream"));
   m.def("softmax_rows", [](uintptr_t x, int rows, int cols, uintptr_t y, uintptr_t amax, uintptr_t stream) {
     SoftmaxRows(P<const float>(x), rows, cols, P<float>(y), P<int64_t>(amax), P<void>(stream));
   });

@@ -197,6 +197,42 @@ struct RnnArgs {
   int coupled = 0;              // LSTM input_forget: f = 1 - i
 };
 int RnnMfma(const RnnArgs& a, void* stream);
+// K25: fused row normalisation (norm_rows.hip), dtype 0 fp32 / 1 fp16 / 2 bf16 for the activation, the outputs
+// and the embedding tables; bias / gamma / beta carry their own dtype code. Per row r of N <= 8192 elements:
+//   v = x[r] | x[r] + skip[r % skip_rows] (+ bias[N]) | word[ids[r]] + pos[pos_ids[r]] (+ seg[seg_ids[r]])
+//   y[r] = (v - mean) * inv_std * gamma + beta   (rms: mean = 0, inv = rsqrt(mean(v^2) + eps), no beta)
+// in fp32 with two-pass statistics. The source is the gather when word is set, the skip form when skip is
+// set. x and skip rows have unit inner stride and pitches x_rs / skip_rs in elements; the tables and the
+// outputs are contiguous with pitch N. pos_ids null: row r takes position r % S. ids are int32 or int64
+// (ids64) and are clamped to their table before use. Optional outputs: sum (v rounded once to the activation
+// dtype), mean and inv (fp32 [rows]). 16-byte accesses are used when N and every pointer and pitch allow
+// them. Returns 0, or -4 when not supported (N > 8192, empty, inconsistent operands).
+struct NormRowsArgs {
+  const void* x = nullptr;
+  const void* skip = nullptr;
+  const void* bias = nullptr;
+  const void* gamma = nullptr;
+  const void* beta = nullptr;
+  void* y = nullptr;
+  void* sum = nullptr;
+  float* mean = nullptr;
+  float* inv = nullptr;
+  const void* ids = nullptr;
+  const void* pos_ids = nullptr;
+  const void* seg_ids = nullptr;
+  const void* word = nullptr;
+  const void* pos = nullptr;
+  const void* seg = nullptr;
+  int64_t rows = 0, x_rs = 0, skip_rs = 0, skip_rows = 0;
+  int N = 0, rms = 0, ids64 = 0, S = 1, word_rows = 0, pos_rows = 0, seg_rows = 0;
+  int bias_dt = 0, gamma_dt = 0, beta_dt = 0;
+  float eps = 0.f;
+};
+int NormRows(const NormRowsArgs& a, int dtype, void* stream);
+// y = act(x + bias[N]) over rows of pitch x_rs, y contiguous; bias may be null and has its own dtype code.
+// mode 0 erf GELU, 1 tanh GELU, 2 v * sigmoid(alpha * v); fp32 math. Returns 0, or -4 when not supported.
+int BiasAct(const void* x, int64_t x_rs, const void* bias, int bias_dt, void* y, int64_t rows, int N, int mode,
+            float alpha, int dtype, void* stream);
 // Direct grouped / depthwise NHWC convolution (conv_direct.hip): x [B,H,W,C], w [Cout][R][S][C/groups],
 // y [B,OH,OW,Cout]; fp32 accumulation; y = conv + bias, relu (1: before the residual add, 2: after), + res.
 struct GroupConvArgs {

@@ -14,6 +14,7 @@ compute dtype; the fused conv/epilogue variants produced by the optimizer
 from __future__ import annotations
 
 import math
+import os
 from typing import Any, Callable, Dict, List
 
 import numpy as np
@@ -141,7 +142,41 @@ OPS["ThresholdedRelu"] = lambda rt, at, x: [torch.where(x[0] > at.get("alpha", 1
 OPS["HardSigmoid"] = lambda rt, at, x: [torch.clamp(at.get("alpha", 0.2) * x[0] + at.get("beta", 0.5), 0, 1)]
 OPS["HardSwish"] = lambda rt, at, x: [Fn.hardswish(x[0])]
 OPS["Mish"] = lambda rt, at, x: [Fn.mish(x[0])]
-OPS["Gelu"] = lambda rt, at, x: [Fn.gelu(x[0], approximate="tanh" if at.get("approximate") == "tanh" else "none")]
+
+
+def _norm_kernels(t):
+    """ops.norm (the fused row-normalisation and bias-activation kernels, K25) when t is a device tensor, else
+    None: the operator runs its torch body. SML_NORM=0 forces the torch bodies."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda) or os.environ.get("SML_NORM", "1") == "0":
+        return None
+    from ..ops import norm
+
+    return norm
+
+
+def _fused_act(v, bias, mode: str, alpha: float = 1.702):
+    """ops.norm.bias_act(v, bias) when the kernel takes the operands and the torch body would return v's
+    dtype, else None. bias: None or a device tensor [N] over v's last dimension."""
+    nk = _norm_kernels(v)
+    if nk is None:
+        return None
+    if bias is not None and not (bias.dim() == 1 and v.dim() and bias.shape[0] == v.shape[-1]
+                                 and bias.is_floating_point() and torch.promote_types(v.dtype, bias.dtype) == v.dtype):
+        return None
+    return nk.bias_act(v, bias, mode, alpha) if nk.supported(v, bias=bias) else None
+
+
+def _gelu_torch(v, approximate: str):
+    return Fn.gelu(v, approximate=approximate)
+
+
+@op("Gelu")
+def _gelu(rt, at, x):
+    approximate = "tanh" if at.get("approximate") == "tanh" else "none"
+    y = _fused_act(x[0], None, "tanh" if approximate == "tanh" else "erf")
+    return [_gelu_torch(x[0], approximate) if y is None else y]
+
+
 OPS["PRelu"] = lambda rt, at, x: [torch.where(x[0] >= 0, x[0], x[0] * _same_dev(x[1].to(x[0].dtype), x[0])[0])]
 OPS["Identity"] = lambda rt, at, x: [x[0]]
 OPS["Dropout"] = lambda rt, at, x: [x[0], torch.ones_like(x[0], dtype=torch.bool)]
@@ -819,15 +854,26 @@ def _inorm(rt, at, x):
                              eps=at.get("epsilon", 1e-5))]
 
 
+def _layer_norm_torch(t, w, b, axis: int, eps: float):
+    w = w.to(t.device, t.dtype) if w is not None else None
+    b = b.to(t.device, t.dtype) if b is not None else None
+    return Fn.layer_norm(t, t.shape[axis:], w, b, eps)
+
+
 @op("LayerNormalization")
 def _lnorm(rt, at, x):
     t = x[0]
     axis = at.get("axis", -1)
     axis = axis + t.dim() if axis < 0 else axis
-    shp = t.shape[axis:]
-    w = x[1].to(t.device, t.dtype) if len(x) > 1 and x[1] is not None else None
-    b = x[2].to(t.device, t.dtype) if len(x) > 2 and x[2] is not None else None
-    return [Fn.layer_norm(t, shp, w, b, at.get("epsilon", 1e-5))]
+    w = x[1] if len(x) > 1 and x[1] is not None else None
+    b = x[2] if len(x) > 2 and x[2] is not None else None
+    eps = at.get("epsilon", 1e-5)
+    nk = _norm_kernels(t)
+    if nk is not None and 0 <= axis < t.dim():
+        wd, bd = (p if p is None else p.to(t.device) for p in (w, b))
+        if math.prod(t.shape[axis:]) <= nk.PLAIN_LN_MAX_N and nk.supported(t, wd, bd, axis=axis):
+            return [nk.layer_norm(t, wd, bd, eps, axis=axis)]
+    return [_layer_norm_torch(t, w, b, axis, eps)]
 
 
 @op("LRN")

@@ -34,7 +34,7 @@ import torch
 import torch.nn.functional as Fn
 
 from . import proto as P
-from .ops import OPS, TORCH_OF, _ints, _to_np, op
+from .ops import OPS, TORCH_OF, _fused_act, _ints, _norm_kernels, _to_np, op
 
 # ops whose outputs' shapes / control flow depend on tensor values (or that read values on the host): a graph
 # containing one is run eagerly, never captured into a hipGraph (a host sync inside a capture invalidates it)
@@ -803,9 +803,25 @@ def _rms(t: torch.Tensor, scale, axis: int, eps: float):
     return y.to(t.dtype), inv
 
 
+def _rms_fused(t: torch.Tensor, scale, axis: int, eps: float, skip=None, bias=None, want_sum: bool = False):
+    """ops.norm.layer_norm(rms=True) -> (y, sum, None, inv) when the operands are on the device and the kernel
+    (K25) takes them, else None: the operator runs _rms(). SML_NORM=0 forces _rms()."""
+    nk = _norm_kernels(t)
+    if nk is None or not -t.dim() <= axis < t.dim():
+        return None
+    scale = None if scale is None else _t(scale, t.device)
+    if not nk.supported(t, scale, skip=skip, bias=bias, axis=axis, fast_only=True):
+        return None
+    return nk.layer_norm(t, scale, None, eps, skip=skip, bias=bias, rms=True, want_sum=want_sum, want_stats=True,
+                         axis=axis)
+
+
 @op("RMSNormalization", "SimplifiedLayerNormalization")
 def _rmsnorm(rt, at, x):
-    y, inv = _rms(_t(x[0]), x[1] if len(x) > 1 else None, int(at.get("axis", -1)), float(at.get("epsilon", 1e-5)))
+    t, scale = _t(x[0]), x[1] if len(x) > 1 else None
+    axis, eps = int(at.get("axis", -1)), float(at.get("epsilon", 1e-5))
+    out = _rms_fused(t, scale, axis, eps)
+    y, inv = (out[0], out[3]) if out is not None else _rms(t, scale, axis, eps)
     return [y, inv][:max(1, rt.node_num_outputs)]
 
 
@@ -1128,24 +1144,38 @@ def _fused_matmul(rt, at, x):
     return [float(at.get("alpha", 1.0)) * torch.matmul(a, b.to(a.dtype))]
 
 
+def _fast_gelu_torch(v, bias):
+    return _gelu_tanh(v if bias is None else v + bias)
+
+
 @op("FastGelu")
 def _fast_gelu(rt, at, x):
     v = _t(x[0])
-    if len(x) > 1 and x[1] is not None:
-        v = v + _t(x[1], v.device, v.dtype)
-    return [_gelu_tanh(v)]
+    bias = _t(x[1], v.device, v.dtype) if len(x) > 1 and x[1] is not None else None
+    y = _fused_act(v, bias, "tanh")
+    return [_fast_gelu_torch(v, bias) if y is None else y]
+
+
+def _bias_gelu_torch(v, bias):
+    return Fn.gelu(v + bias)
 
 
 @op("BiasGelu")
 def _bias_gelu(rt, at, x):
-    v = _t(x[0]) + _t(x[1], _dev(x))
-    return [Fn.gelu(v)]
+    v, bias = _t(x[0]), _t(x[1], _dev(x))
+    y = _fused_act(v, bias, "erf") if bias.device == v.device else None
+    return [_bias_gelu_torch(v, bias) if y is None else y]
+
+
+def _quick_gelu_torch(v, alpha: float):
+    return v * torch.sigmoid(alpha * v)
 
 
 @op("QuickGelu")
 def _quick_gelu(rt, at, x):
-    v = _t(x[0])
-    return [v * torch.sigmoid(float(at.get("alpha", 1.702)) * v)]
+    v, alpha = _t(x[0]), float(at.get("alpha", 1.702))
+    y = _fused_act(v, None, "quick", alpha)
+    return [_quick_gelu_torch(v, alpha) if y is None else y]
 
 
 def _skip_sum(x):
@@ -1157,10 +1187,29 @@ def _skip_sum(x):
     return s
 
 
+def _skip_operands(t: torch.Tensor, skip, bias):
+    """skip and bias of the skip layer norms as the kernel reads them: on t's device, skip in t's dtype"""
+    return _t(skip, t.device, t.dtype), None if bias is None else _t(bias, t.device)
+
+
 @op("SkipLayerNormalization")
 def _skip_ln(rt, at, x):
+    eps, nout = float(at.get("epsilon", 1e-12)), max(1, rt.node_num_outputs)
+    t = _t(x[0])
+    nk = _norm_kernels(t)
+    if nk is not None:
+        skip, bias = _skip_operands(t, x[1], x[4] if len(x) > 4 else None)
+        gamma = _t(x[2], t.device)
+        beta = _t(x[3], t.device) if len(x) > 3 and x[3] is not None else None
+        if nk.supported(t, gamma, beta, skip=skip, bias=bias, fast_only=True):
+            y, s, mean, inv = nk.layer_norm(t, gamma, beta, eps, skip=skip, bias=bias, want_sum=nout > 3,
+                                            want_stats=nout > 1)
+            return [y, mean, inv, s][:nout]
+    return _skip_ln_torch(x, eps)[:nout]
+
+
+def _skip_ln_torch(x, eps: float):
     s = _skip_sum(x)
-    eps = float(at.get("epsilon", 1e-12))
     sf = s.to(torch.float32)
     mean = sf.mean(-1, keepdim=True)
     var = ((sf - mean) ** 2).mean(-1, keepdim=True)
@@ -1168,15 +1217,22 @@ def _skip_ln(rt, at, x):
     y = (sf - mean) * inv * _t(x[2], s.device, torch.float32)
     if len(x) > 3 and x[3] is not None:
         y = y + _t(x[3], s.device, torch.float32)
-    return [y.to(s.dtype), mean, inv, s][:max(1, rt.node_num_outputs)]
+    return [y.to(s.dtype), mean, inv, s]
 
 
 @op("SkipSimplifiedLayerNormalization")
 def _skip_rms(rt, at, x):
-    xs = list(x) + [None] * (5 - len(x))
-    s = _skip_sum([xs[0], xs[1], None, None, xs[3]])  # inputs: input, skip, gamma, bias
-    y, inv = _rms(s, xs[2], -1, float(at.get("epsilon", 1e-12)))
-    return [y, None, inv, s][:max(1, rt.node_num_outputs)]
+    xs = list(x) + [None] * (5 - len(x))  # inputs: input, skip, gamma, bias
+    eps, nout = float(at.get("epsilon", 1e-12)), max(1, rt.node_num_outputs)
+    t = _t(xs[0])
+    if _norm_kernels(t) is not None:
+        skip, bias = _skip_operands(t, xs[1], xs[3])
+        out = _rms_fused(t, xs[2], -1, eps, skip, bias, want_sum=nout > 3)
+        if out is not None:
+            return [out[0], None, out[3], out[1]][:nout]
+    s = _skip_sum([xs[0], xs[1], None, None, xs[3]])
+    y, inv = _rms(s, xs[2], -1, eps)
+    return [y, None, inv, s][:nout]
 
 
 @op("EmbedLayerNormalization")
@@ -1186,6 +1242,37 @@ def _embed_ln(rt, at, x):
     dev = _dev([xs[2]])
     ids = ids.to(dev)
     word = _t(xs[2], dev)
+    B, S = ids.shape
+    eps = float(at.get("epsilon", 1e-12))
+    y, emb = _embed_ln_fused(ids, xs, word, eps, rt.node_num_outputs > 2) or _embed_ln_torch(ids, xs, word, eps)
+    if xs[7] is not None:
+        mask_index = _t(xs[7], dev).to(torch.int32).sum(-1).to(torch.int32)
+    else:
+        mask_index = torch.full((B,), S, dtype=torch.int32, device=dev)
+    return [y, mask_index, emb][:max(1, rt.node_num_outputs)]
+
+
+def _embed_ln_fused(ids, xs, word, eps: float, want_sum: bool):
+    """ops.norm.embed_layer_norm -> (y, embedding sum | None) when the tables are on the device and the kernel
+    (K25) takes them, else None: the operator runs _embed_ln_torch(). SML_NORM=0 forces that."""
+    nk = _norm_kernels(word)
+    if nk is None or ids.dim() != 2:
+        return None
+    dev = word.device
+    seg_on = xs[1] is not None and xs[4] is not None
+    seg_ids = _t(xs[1], dev).long() if seg_on else None
+    seg = _t(xs[4], dev, word.dtype) if seg_on else None
+    pos = _t(xs[3], dev, word.dtype)
+    pos_ids = _t(xs[8], dev).long() if xs[8] is not None else None
+    gamma, beta = _t(xs[5], dev), _t(xs[6], dev)
+    if not nk.embed_supported(ids, seg_ids, word, pos, seg, gamma, beta, pos_ids, fast_only=True):
+        return None
+    out = nk.embed_layer_norm(ids, seg_ids, word, pos, seg, gamma, beta, eps, pos_ids, want_sum)
+    return out if want_sum else (out, None)
+
+
+def _embed_ln_torch(ids, xs, word, eps: float):
+    dev = word.device
     emb = word[ids]
     B, S = ids.shape
     pos_ids = _t(xs[8], dev).long() if xs[8] is not None else torch.arange(S, device=dev).expand(B, S)
@@ -1193,12 +1280,8 @@ def _embed_ln(rt, at, x):
     if xs[1] is not None and xs[4] is not None:
         emb = emb + _t(xs[4], dev, emb.dtype)[_t(xs[1], dev).long()]
     y = Fn.layer_norm(emb.to(torch.float32), (emb.shape[-1],), _t(xs[5], dev, torch.float32),
-                      _t(xs[6], dev, torch.float32), float(at.get("epsilon", 1e-12))).to(emb.dtype)
-    if xs[7] is not None:
-        mask_index = _t(xs[7], dev).to(torch.int32).sum(-1).to(torch.int32)
-    else:
-        mask_index = torch.full((B,), S, dtype=torch.int32, device=dev)
-    return [y, mask_index, emb][:max(1, rt.node_num_outputs)]
+                      _t(xs[6], dev, torch.float32), eps).to(emb.dtype)
+    return y, emb
 
 
 def _attend(q, k, v, heads: int, scale: Optional[float], mask_add: Optional[torch.Tensor], causal: bool):
