@@ -256,6 +256,34 @@ PYBIND11_MODULE(_nn, m) {
     return true;
   }, pybind11::arg("x"), pybind11::arg("bias"), pybind11::arg("y"), pybind11::arg("dims"), pybind11::arg("alpha"),
      pybind11::arg("stream"));
+  // fused forest walk (K26). ptrs (0 = absent): x, nodes, list, tree_off, tree_depth, chunk_tree, base, out,
+  // label, labels, ws. dims: n, F, x row pitch, T, C, K, average, post, binary, classifier, launch, ws floats.
+  // Returns false when the kernel does not take the problem (nothing was launched).
+  m.def("forest_walk", [](std::vector<uintptr_t> ptrs, std::vector<int64_t> dims, uintptr_t stream) {
+    if (ptrs.size() != 11 || dims.size() != 12) throw std::invalid_argument("forest_walk: 11 ptrs, 12 dims");
+    for (size_t i : {1, 3, 4, 5, 6, 7, 8, 9, 10})
+      if (dims[i] < 0 || dims[i] > INT32_MAX) return false;
+    ForestArgs a;
+    a.x = P<const float>(ptrs[0]); a.nodes = P<const void>(ptrs[1]); a.list = P<const void>(ptrs[2]);
+    a.tree_off = P<const int32_t>(ptrs[3]); a.tree_depth = P<const int32_t>(ptrs[4]);
+    a.chunk_tree = P<const int32_t>(ptrs[5]); a.base = P<const float>(ptrs[6]); a.out = P<float>(ptrs[7]);
+    a.label = P<int64_t>(ptrs[8]); a.labels = P<const int64_t>(ptrs[9]); a.ws = P<float>(ptrs[10]);
+    a.n = dims[0]; a.F = static_cast<int>(dims[1]); a.x_rs = dims[2]; a.T = static_cast<int>(dims[3]);
+    a.C = static_cast<int>(dims[4]); a.K = static_cast<int>(dims[5]); a.average = static_cast<int>(dims[6]);
+    a.post = static_cast<int>(dims[7]); a.binary = static_cast<int>(dims[8]);
+    a.classifier = static_cast<int>(dims[9]); a.launch = static_cast<int>(dims[10]); a.ws_floats = dims[11];
+    const int rc = ForestWalk(a, P<void>(stream));
+    if (rc == -4) return false;
+    if (rc != 0) throw std::runtime_error("forest_walk failed (rc=" + std::to_string(rc) + ")");
+    return true;
+  }, pybind11::arg("ptrs"), pybind11::arg("dims"), pybind11::arg("stream"));
+  // (launch shape 1 row-parallel / 2 tree-parallel, workspace slices) of forest_walk; shape -4: not supported
+  m.def("forest_plan", [](int64_t n, int64_t F, int64_t T, int64_t K, int launch) {
+    int slices = 0;
+    if (F > INT32_MAX || T > INT32_MAX || K > INT32_MAX) return std::make_pair(-4, 0);
+    const int shape = ForestWalkPlan(n, static_cast<int>(F), static_cast<int>(T), static_cast<int>(K), launch, &slices);
+    return std::make_pair(shape, slices);
+  });
   m.def("softmax_rows", [](uintptr_t x, int rows, int cols, uintptr_t y, uintptr_t amax, uintptr_t stream) {
     SoftmaxRows(P<const float>(x), rows, cols, P<float>(y), P<int64_t>(amax), P<void>(stream));
   });

@@ -233,6 +233,43 @@ int NormRows(const NormRowsArgs& a, int dtype, void* stream);
 // mode 0 erf GELU, 1 tanh GELU, 2 v * sigmoid(alpha * v); fp32 math. Returns 0, or -4 when not supported.
 int BiasAct(const void* x, int64_t x_rs, const void* bias, int bias_dt, void* y, int64_t rows, int N, int mode,
             float alpha, int dtype, void* stream);
+// K26: fused forest walk for the ai.onnx.ml TreeEnsemble operators (forest_walk.hip; the record layout is
+// described there). x is fp32 [n, F] with unit inner stride and row pitch x_rs; nodes are 16-byte records
+// (16-byte aligned), list 8-byte (id, weight bits) pairs of the leaves with several entries (may be null when
+// there are none), tree_off int32 [T + 1], tree_depth int32 [T], chunk_tree int32 [C + 1]. Scores are the fp32
+// sum over the trees of the reached leaves' entries, divided by T (average), plus base [K] (may be null), then
+// post 0 none / 1 logistic / 2 softmax. out is fp32 [n, K], or [n, 2] for binary (K = 1: [1 - p, p] under
+// logistic, else [-s, s]; label index s > 0). classifier: label int64 [n] gets labels[argmax] (the index when
+// labels is null), lowest index on ties. launch 0 picks the launch shape by batch size, 1 forces the
+// row-parallel kernel, 2 the tree-parallel one, which needs ws: ForestWalkPlan's slices * n * K floats.
+// The caller guarantees what the device arrays hold: feature ids < F, child indices inside their tree, ids
+// < K, list ranges inside the list. Returns 0, or -4 when not supported (K > 192, K > 48 tree-parallel, a
+// workspace too small, an empty dimension).
+constexpr int kForestChunkNodes = 1024;     // nodes of the LDS forest buffer of the row-parallel kernel
+constexpr int kForestRegK = 8;              // largest K whose scores are kept in registers
+constexpr int kForestRowBlocksPerCu = 1;    // launch 0: row-parallel from this many row tiles per CU on
+struct ForestArgs {
+  const float* x = nullptr;
+  int64_t x_rs = 0, n = 0;
+  const void* nodes = nullptr;
+  const void* list = nullptr;
+  const int32_t* tree_off = nullptr;
+  const int32_t* tree_depth = nullptr;
+  const int32_t* chunk_tree = nullptr;
+  int F = 0, T = 0, C = 0, K = 0;
+  const float* base = nullptr;
+  int average = 0, post = 0, binary = 0, classifier = 0;
+  float* out = nullptr;
+  int64_t* label = nullptr;
+  const int64_t* labels = nullptr;
+  int launch = 0;
+  float* ws = nullptr;
+  int64_t ws_floats = 0;
+};
+// the launch shape ForestWalk would take (1 row-parallel, 2 tree-parallel; -4: not supported) and, for the
+// tree-parallel one, the number of forest slices of its workspace (0 otherwise)
+int ForestWalkPlan(int64_t n, int F, int T, int K, int launch, int* slices);
+int ForestWalk(const ForestArgs& a, void* stream);
 // Direct grouped / depthwise NHWC convolution (conv_direct.hip): x [B,H,W,C], w [Cout][R][S][C/groups],
 // y [B,OH,OW,Cout]; fp32 accumulation; y = conv + bias, relu (1: before the residual add, 2: after), + res.
 struct GroupConvArgs {

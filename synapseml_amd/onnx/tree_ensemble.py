@@ -1,8 +1,12 @@
 """ai.onnx.ml TreeEnsembleRegressor / TreeEnsembleClassifier (the form in
-which LightGBM/sklearn tree models are exported to ONNX). Every (row, tree)
-pair walks its tree in lock-step — one gather per level over flattened node
-arrays — so a whole batch is a handful of device-wide tensor ops."""
+which LightGBM/sklearn tree models are exported to ONNX). Device tensors run
+on the fused forest-walk kernel (K26, ops/trees.py). The torch body serves
+everything else: every (row, tree) pair walks its tree in lock-step — one
+gather per level over flattened node arrays — so a whole batch is a handful
+of device-wide tensor ops."""
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -58,10 +62,41 @@ def _max_depth(ti, fi, modes, roots):
     return best
 
 
+def _fused(at, classifier: bool, X):
+    """The operator's outputs from ops.trees (the fused forest-walk kernel, K26) when X is a device tensor and
+    the kernel serves the node, else None: the operator runs _walk_torch(). The packed forest is cached with
+    the node, its device tensors per device. SML_TREES=0 forces _walk_torch()."""
+    if not (isinstance(X, torch.Tensor) and X.is_cuda) or os.environ.get("SML_TREES", "1") == "0":
+        return None
+    from ..ops import trees
+
+    cache = at.setdefault("__compiled__", {})
+    if "forest" not in cache:
+        cache["forest"] = trees.pack(at, classifier)
+    forest = cache["forest"]
+    X = X.to(torch.float32)
+    if X.dim() == 1:
+        X = X.unsqueeze(0)
+    if forest is None or X.dim() != 2 or not X.numel():
+        return None
+    if X.shape[1] > 1 and X.stride(1) != 1:
+        X = X.contiguous()
+    out, label = trees.tree_ensemble(X, forest)  # raises ValueError on a feature id outside X
+    if not classifier:
+        return [out]
+    if isinstance(forest.labels[0], str):
+        return [np.asarray(forest.labels)[label.cpu().numpy()].astype(object), out]
+    return [label, out]
+
+
 def run_tree_ensemble(rt, at, x):
     classifier = rt.op_type == "TreeEnsembleClassifier"
+    fused = _fused(at, classifier, x[0])
+    return fused if fused is not None else _walk_torch(at, classifier, x[0])
+
+
+def _walk_torch(at, classifier: bool, X):
     cache = at.setdefault("__compiled__", {})
-    X = x[0]
     dev = X.device if isinstance(X, torch.Tensor) else torch.device("cpu")
     if dev not in cache:
         c = _compile(at, classifier)
