@@ -284,6 +284,29 @@ PYBIND11_MODULE(_nn, m) {
     const int shape = ForestWalkPlan(n, static_cast<int>(F), static_cast<int>(T), static_cast<int>(K), launch, &slices);
     return std::make_pair(shape, slices);
   });
+  // one ALS half-sweep (K27). ptrs (0 = absent): indices, val, tasks, red, Y, X, yty, ws. dims: nX, nY, k, kp,
+  // ntasks, nred, slots, ws doubles, seg_len, implicit, nonnegative. scalars: lam, alpha. Returns false when the
+  // kernel does not take the problem (nothing was launched).
+  m.def("als_sweep", [](std::vector<uintptr_t> ptrs, std::vector<int64_t> dims, std::vector<double> scalars,
+                        uintptr_t stream) {
+    if (ptrs.size() != 8 || dims.size() != 11 || scalars.size() != 2)
+      throw std::invalid_argument("als_sweep: 8 ptrs, 11 dims, 2 scalars");
+    for (size_t i : {2, 3, 8, 9, 10})
+      if (dims[i] < 0 || dims[i] > INT32_MAX) return false;
+    if (ptrs[4] % 128 || ptrs[5] % 128) return false;
+    AlsArgs a;
+    a.indices = P<const int32_t>(ptrs[0]); a.val = P<const double>(ptrs[1]); a.tasks = P<const int64_t>(ptrs[2]);
+    a.red = P<const int64_t>(ptrs[3]); a.Y = P<const double>(ptrs[4]); a.X = P<double>(ptrs[5]);
+    a.yty = P<double>(ptrs[6]); a.ws = P<double>(ptrs[7]);
+    a.nX = dims[0]; a.nY = dims[1]; a.k = static_cast<int>(dims[2]); a.kp = static_cast<int>(dims[3]);
+    a.ntasks = dims[4]; a.nred = dims[5]; a.slots = dims[6]; a.ws_doubles = dims[7];
+    a.seg_len = static_cast<int>(dims[8]); a.implicit = static_cast<int>(dims[9]);
+    a.nonnegative = static_cast<int>(dims[10]); a.lam = scalars[0]; a.alpha = scalars[1];
+    const int rc = AlsSweep(a, P<void>(stream));
+    if (rc == -4) return false;
+    if (rc != 0) throw std::runtime_error("als_sweep failed (rc=" + std::to_string(rc) + ")");
+    return true;
+  }, pybind11::arg("ptrs"), pybind11::arg("dims"), pybind11::arg("scalars"), pybind11::arg("stream"));
   m.def("softmax_rows", [](uintptr_t x, int rows, int cols, uintptr_t y, uintptr_t amax, uintptr_t stream) {
     SoftmaxRows(P<const float>(x), rows, cols, P<float>(y), P<int64_t>(amax), P<void>(stream));
   });

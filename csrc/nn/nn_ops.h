@@ -270,6 +270,30 @@ struct ForestArgs {
 // tree-parallel one, the number of forest slices of its workspace (0 otherwise)
 int ForestWalkPlan(int64_t n, int F, int T, int K, int launch, int* slices);
 int ForestWalk(const ForestArgs& a, void* stream);
+// K27: one ALS half-sweep (als_mfma.hip): X[row] of every task's row is solved from the factors Y of the other
+// side. X [nX, kp] and Y [nY, kp] are fp64 with kp = k padded to a multiple of 16 and zero pad columns, both
+// 128-byte aligned. indices int32 / val fp64 are the CSR payload of X's side; tasks int64 [ntasks, 4] are
+// (row, first nonzero, length <= seg_len, slot or -1), red int64 [nred, 4] are (row, first slot, slots, n_r) of
+// the rows cut into segments (may be null when nred == 0); slots is the number of workspace slots the tasks
+// name. ws holds max(slots, implicit ? ceil(nY / seg_len) : 0) * (kp kp + kp) doubles; yty [kp, kp] is written
+// and read by an implicit sweep. The caller guarantees what the device arrays hold: indices in [0, nY), rows in
+// [0, nX), nonzero ranges inside indices / val, slot ranges inside slots. Returns 0, -3 when a launch fails, or
+// -4 when not supported (k outside 1 .. 64, lam not positive and finite, a workspace too small).
+constexpr int kAlsMaxRank = 64;
+struct AlsArgs {
+  const int32_t* indices = nullptr;
+  const double* val = nullptr;
+  const int64_t* tasks = nullptr;
+  const int64_t* red = nullptr;
+  const double* Y = nullptr;
+  double* X = nullptr;
+  double* yty = nullptr;
+  double* ws = nullptr;
+  int64_t nX = 0, nY = 0, ntasks = 0, nred = 0, slots = 0, ws_doubles = 0;
+  int k = 0, kp = 0, seg_len = 0, implicit = 0, nonnegative = 0;
+  double lam = 0.0, alpha = 0.0;
+};
+int AlsSweep(const AlsArgs& a, void* stream);
 // Direct grouped / depthwise NHWC convolution (conv_direct.hip): x [B,H,W,C], w [Cout][R][S][C/groups],
 // y [B,OH,OW,Cout]; fp32 accumulation; y = conv + bias, relu (1: before the residual add, 2: after), + res.
 struct GroupConvArgs {

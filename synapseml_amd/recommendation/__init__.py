@@ -230,17 +230,12 @@ class ALS(Estimator, RecommendationParams, HasPredictionCol, HasSeed):
     nonnegative = Param("whether to use nonnegative constraint for least squares", False, T.toBoolean)
     coldStartStrategy = Param("nan | drop", "nan", T.toString)
 
-    def _fit(self, df):
+    def _dense_sweeps(self, U, V, u, i, r):
+        """The dense body: ratings scattered into nU x nI matrices, every half-sweep one batched GEMM against the
+        Y (x) Y outer products and one batched solve. Updates U and V in place."""
         import torch
 
-        dev = _torch_dev()
-        u = np.asarray(df[self.getUserCol()], np.float64).astype(np.int64)
-        i = np.asarray(df[self.getItemCol()], np.float64).astype(np.int64)
-        r = np.asarray(df[self.getRatingCol()], np.float64) if self.getRatingCol() in df else np.ones(len(u))
-        nU, nI, k = int(u.max()) + 1, int(i.max()) + 1, self.getRank()
-        g = torch.Generator().manual_seed(self.getSeed())
-        U = (torch.rand(nU, k, generator=g, dtype=torch.float64) * 0.1).to(dev)
-        V = (torch.rand(nI, k, generator=g, dtype=torch.float64) * 0.1).to(dev)
+        dev, (nU, k), nI = U.device, U.shape, V.shape[0]
         R = torch.zeros(nU, nI, dtype=torch.float64, device=dev)
         M = torch.zeros(nU, nI, dtype=torch.float64, device=dev)
         R[torch.as_tensor(u, device=dev), torch.as_tensor(i, device=dev)] = torch.as_tensor(r, device=dev)
@@ -271,10 +266,42 @@ class ALS(Estimator, RecommendationParams, HasPredictionCol, HasSeed):
                 if not implicit:
                     sol = torch.where((Mm.sum(1) > 0)[:, None], sol, X)
                 X.copy_(sol.clamp(min=0) if nonneg else sol)
+
+    def _fit(self, df):
+        import os
+
+        import torch
+
+        dev = _torch_dev()
+        u = np.asarray(df[self.getUserCol()], np.float64).astype(np.int64)
+        i = np.asarray(df[self.getItemCol()], np.float64).astype(np.int64)
+        r = np.asarray(df[self.getRatingCol()], np.float64) if self.getRatingCol() in df else np.ones(len(u))
+        nU, nI, k = int(u.max()) + 1, int(i.max()) + 1, self.getRank()
+        g = torch.Generator().manual_seed(self.getSeed())
+        U = torch.rand(nU, k, generator=g, dtype=torch.float64) * 0.1
+        V = torch.rand(nI, k, generator=g, dtype=torch.float64) * 0.1
+        # On a GPU the sweeps run on the fused sparse kernel (K27, ops.als) wherever it serves the fit; SML_ALS=0
+        # and everything it declines keep the dense body.
+        sparse = False
+        if dev.type == "cuda" and os.environ.get("SML_ALS", "1") != "0":
+            from ..ops import als as als_ops
+
+            sparse = als_ops.supported(dev, k, self.getRegParam(), u, i, r, self.getImplicitPrefs())
+        if sparse:
+            prep = als_ops.prepare(u, i, r, nU, nI)
+            U, V = als_ops.factors(U, dev), als_ops.factors(V, dev)
+            for _ in range(self.getMaxIter()):
+                for side in (0, 1):
+                    X, Y = (U, V) if side == 0 else (V, U)
+                    als_ops.half_sweep(prep, side, X, Y, self.getRegParam(), self.getAlpha(),
+                                       self.getImplicitPrefs(), self.getNonnegative())
+        else:
+            U, V = U.to(dev), V.to(dev)
+            self._dense_sweeps(U, V, u, i, r)
         model = ALSModel(userCol=self.getUserCol(), itemCol=self.getItemCol(), ratingCol=self.getRatingCol(),
                          predictionCol=self.getPredictionCol(), coldStartStrategy=self.getColdStartStrategy())
-        model.set("userFactors", U.cpu().numpy())
-        model.set("itemFactors", V.cpu().numpy())
+        model.set("userFactors", U.contiguous().cpu().numpy())
+        model.set("itemFactors", V.contiguous().cpu().numpy())
         return model
 
 

@@ -77,7 +77,7 @@ MODULES = {
     "_nn": (
         "csrc/nn",
         ["nn_bindings.cpp", "nn_ops.hip", "conv_mfma.hip", "gemm_mfma.hip", "conv_direct.hip", "qgemm_mfma.hip",
-         "attn_mfma.hip", "mips_topk.hip", "rnn_mfma.hip", "norm_rows.hip", "forest_walk.hip"],
+         "attn_mfma.hip", "mips_topk.hip", "rnn_mfma.hip", "norm_rows.hip", "forest_walk.hip", "als_mfma.hip"],
         [],
     ),
 }
